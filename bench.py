@@ -225,6 +225,28 @@ def emit_json_line(out):
         pass
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, solver):
+    """--dump-outputs DIR: what the timed path handed its caller after the last timed step -- the iterate of the preprocessed model
+    (x, y, z, s) and its scalars tau, kap, mu and the accepted step length alpha -- as DIR/<name>.npy (float64), so that two builds can
+    be compared output for output on the same seeded instance (config 2: 0.4 MB).  Empty arrays (y at p = 0) are not written.  Past
+    64 MB in all, each long array is replaced by a fixed sample of its entries (seeded by its length)."""
+    pt = solver.point
+    arrays = {"x": pt.x, "y": pt.y, "z": pt.z, "s": pt.s,
+              "tau": [pt.tau], "kap": [pt.kap], "mu": [solver.mu], "alpha": [solver.stepper.prev_alpha]}
+    arrays = {k: np.array(v, dtype=np.float64) for k, v in arrays.items() if len(v)}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_CAP_BYTES:
+        keep = DUMP_CAP_BYTES // 8 // len(arrays)
+        for k, a in arrays.items():
+            if a.size > keep:
+                arrays[k] = a[np.sort(np.random.default_rng(a.size).choice(a.size, keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 SITE_NAMES = ["schur_sum", "solve_Gtz", "solve_htz", "residual_fused", "residual_htz", "residual_norm", "constant_column", "screen_a", "screen_b",
               "trial_sums", "trial_closing", "residual_products", "host_requested", "screen_agreement", "schur_incl_pack", "other"]
 
@@ -538,6 +560,8 @@ def run_headline(args, world, rank, local_rank, multi, comm=None):
         comm.allreduce(el, "max")
         elapsed = float(el[0])
     blas_cap.__exit__(None, None, None)   # (the CPU baseline below runs with the full host BLAS pool)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver)
 
     ks = (ctypes.c_double * 8)()
     lib.hyp_get_kernel_stats(ctx, ks)
@@ -917,7 +941,11 @@ def main():
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="N > 1, config 4: skip the secondary record (config 2, K-panel shard)")
     ap.add_argument("--secondary-steps", type=int, default=100)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config 2, or 4 on one GPU: write the iterate and its scalars after the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -925,6 +953,8 @@ def main():
     multi = world > 1 or bool(os.environ.get("HYP_FORCE_DIST"))   # HYP_FORCE_DIST=1: exercise the RCCL path with a single rank
     if args.config is None:
         args.config = "4" if multi else "2"
+    if args.dump_outputs and (args.config not in ("2", "4") or (multi and args.config != "2")):
+        raise SystemExit("--dump-outputs: config 2, or config 4 on one GPU")
     if args.config in ("3b", "3c", "5p", "5d"):
         if multi and args.config not in ("5p", "5d"):
             raise SystemExit("--config %s is a single-GPU line" % args.config)
